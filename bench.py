@@ -15,17 +15,24 @@ rt_tile_owner(tx, ty, N), rt_render_cfg.tile_rank / tile_world), every rank rend
 pixels are packed and gathered to rank 0 over RCCL/xGMI (rustraytracer_amd/dist.py); the gather
 time is reported separately (`gather_ms_per_step`) and is inside the timed region.
 
-One JSON line on rank 0 with
+One JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline (metric, value,
+unit, higher_is_better, dtype, ms_per_step) with what the timed steps themselves counted (rays, device time per step,
+the gather time).  --dump-outputs DIR writes the film of the last timed step (dump_outputs()).  --full adds everything
+that costs runs or work of its own:
+  film_fnv1a    the film of the last timed step as one number; N > 1: film_matches_one_rank (1-spp tiles + gather
+                against rank 0 alone)
   roofline      per kernel group (k_trace / k_shade = the class kernels + the light kernel / k_classify): share of the
                 device time (HIP events), algorithmic bytes per step over that time, and -- from the rocprofv3 PMC
                 passes committed under profiles/, when they belong to the library running now -- the measured HBM
                 fractions (all bytes, reads only).  The top level names the group with the LARGEST share of device
                 time (`kernel`); `frac` is its measured fraction when the profile is current, else the algorithmic one;
-                an algorithmic fraction above 1 (cache hits counted) is never reported as `frac`
-  rays          R1 / R2 / R3 of SURVEY.md 8(d) (extension incl. primary, shadow, MIS probe)
-  cpu_baseline  the oracle in reference-shaped mode on the host cores, bounded sample (rank 0, N = 1 only)
-  extra         (N = 1) the smaller single-GPU configs C2 and C3 measured the same way, for continuity with
-                round 1's numbers
+                an algorithmic fraction above 1 (cache hits counted) is never reported as `frac`; it needs one
+                instrumented render of its own (traversal counters)
+  cpu_baseline  the oracle in reference-shaped mode on the host cores, bounded sample (rank 0, N = 1 only;
+                --no-cpu-baseline drops it)
+  extra         (N = 1, C4) the smaller single-GPU configs C2 and C3 measured the same way, for continuity with
+                round 1's numbers, and the f32 fast mode on the headline workload (--no-extra drops them)
+In every run, `rays` = R1 / R2 / R3 of SURVEY.md 8(d) (extension incl. primary, shadow, MIS probe) per step.
 """
 import argparse
 import json
@@ -280,6 +287,30 @@ def fnv1a_film(d_rgb, d_n):
     return "%016x" % h
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, d_rgb, d_n, rays_last):
+    """What the timed path hands its caller for the last timed step, as .npy files for an output-by-output comparison of
+    two builds: film_rgb.npy (H x W x 3 radiance sums, f64), film_n.npy (H x W sample counts, as f32: exact up to 2^24)
+    and rays.npy (R1 / R2 / R3 of that step, f64).  A film above 64 MB in all (C5) is written as a fixed sample of
+    pixels (seed 0), with their flat indices in film_pixel_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rgb = d_rgb.cpu().numpy().astype(np.float64)
+    n = d_n.cpu().numpy().astype(np.float32)
+    H, W = n.shape
+    per_px = rgb.itemsize * 3 + n.itemsize
+    if H * W * per_px > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - (1 << 20)) // (per_px + 8)
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=k, replace=False))
+        rgb, n = rgb.reshape(-1, 3)[idx], n.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, "film_pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "film_rgb.npy"), rgb)
+    np.save(os.path.join(out_dir, "film_n.npy"), n)
+    np.save(os.path.join(out_dir, "rays.npy"), np.asarray(rays_last, dtype=np.float64))
+
+
 def timed(b, steps, warmup, barrier):
     if warmup == 0 and b.world > 1:
         # one-off set-up that is not the measured work: RCCL connects peers at the first gather (1 spp of the same
@@ -298,6 +329,7 @@ def timed(b, steps, warmup, barrier):
     t0 = time.perf_counter()
     for _ in range(steps):
         st = b.step()
+        acc["last"] = (st.rays_extension, st.rays_shadow, st.rays_probe)
         acc["rays"] += st.rays
         acc["trace_ms"] += st.trace_ms
         acc["kernel_ms"] += st.kernel_ms
@@ -416,11 +448,15 @@ def roofline(b, acc, stc, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c4", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C3 rows")
+    ap.add_argument("--full", action="store_true",
+                    help="also the film hash (and the N > 1 film check), the roofline, the extra rows and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film and ray counts of the last timed step to DIR/*.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C2 / C3 / f32 rows")
     ap.add_argument("--paths-in-flight", type=int, default=0)
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"],
                     help="f32 = the fast mode (RT_PRECISION_F32): reported, not the headline -- the metric is defined on the f64 parity mode")
@@ -430,6 +466,8 @@ def main():
                     help='row-f4 workloads (hdr, hdr1, teapot): "golden" = the committed reference data files under tests/golden/assets, '
                          '"none" = procedural stand-ins, or a directory laid out like the reference\'s data/material')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global ASSETS
     ASSETS = args.assets
 
@@ -487,35 +525,43 @@ def main():
         dv[rank] = local_rank
         dist.all_reduce(dv, op=dist.ReduceOp.SUM)
         devices_all = [int(x) for x in dv.tolist()]
-    r3 = torch.tensor([float(acc["r1"]), float(acc["r2"]), float(acc["r3"])], dtype=torch.float64, device=coll_dev)
+    # per step: R1 / R2 / R3 summed over the steps, and those of the last step (--dump-outputs), over all ranks
+    r3 = torch.tensor([float(acc["r1"]), float(acc["r2"]), float(acc["r3"])] + [float(x) for x in acc["last"]],
+                      dtype=torch.float64, device=coll_dev)
+    per_rank_ms = None
     if world > 1:
         dist.all_reduce(r3, op=dist.ReduceOp.SUM)
-    rays3 = [float(x) for x in r3.tolist()]
-    # the film of the last timed step on rank 0 (N > 1: gathered), as one number
-    film_hash = fnv1a_film(b.d_rgb, b.d_n) if rank == 0 else None
-    film_ok, per_rank_ms = None, None
-    if world > 1:
-        # device time of every rank's own share, and the proof that the gathered film is THE film: the same image at
-        # 1 spp rendered once by all ranks (tiles + gather) and once by rank 0 alone, compared bit for bit -- outside
-        # the timed region
+        # device time of every rank's own share
         pr = torch.zeros(world, dtype=torch.float64, device=coll_dev)
         pr[rank] = acc["kernel_ms"] / args.steps
         dist.all_reduce(pr, op=dist.ReduceOp.SUM)
         per_rank_ms = [float(x) for x in pr.tolist()]
-        cfg_keep = b.cfg
-        b.cfg = rr.make_cfg(b.W, b.H, 1, seed=0, tile_rank=rank, tile_world=world, paths_in_flight=b.pif, precision=b.precision)
-        b.step()
-        if rank == 0:
-            many = (b.d_rgb.clone(), b.d_n.clone())
-            b.cfg = rr.make_cfg(b.W, b.H, 1, seed=0, paths_in_flight=b.pif, precision=b.precision)
-            g = b.gather
-            b.gather = None
+    rays3 = [float(x) for x in r3.tolist()]
+    if args.dump_outputs and rank == 0:
+        # the film of the last timed step (N > 1: gathered on rank 0), before anything below renders into it
+        dump_outputs(args.dump_outputs, b.d_rgb, b.d_n, rays3[3:])
+
+    film_hash = film_ok = None
+    if args.full:
+        # the film of the last timed step on rank 0 (N > 1: gathered), as one number
+        film_hash = fnv1a_film(b.d_rgb, b.d_n) if rank == 0 else None
+        if world > 1:
+            # the proof that the gathered film is THE film: the same image at 1 spp rendered once by all ranks (tiles +
+            # gather) and once by rank 0 alone, compared bit for bit -- outside the timed region
+            cfg_keep = b.cfg
+            b.cfg = rr.make_cfg(b.W, b.H, 1, seed=0, tile_rank=rank, tile_world=world, paths_in_flight=b.pif, precision=b.precision)
             b.step()
-            b.gather = g
-            film_ok = bool(torch.equal(many[0], b.d_rgb) and torch.equal(many[1], b.d_n))
-        b.cfg = cfg_keep
-        barrier()
-    stc = b.counted()
+            if rank == 0:
+                many = (b.d_rgb.clone(), b.d_n.clone())
+                b.cfg = rr.make_cfg(b.W, b.H, 1, seed=0, paths_in_flight=b.pif, precision=b.precision)
+                g = b.gather
+                b.gather = None
+                b.step()
+                b.gather = g
+                film_ok = bool(torch.equal(many[0], b.d_rgb) and torch.equal(many[1], b.d_n))
+            b.cfg = cfg_keep
+            barrier()
+        stc = b.counted()
 
     if rank == 0:
         W, H, spp = b.W, b.H, b.spp
@@ -533,7 +579,10 @@ def main():
                        # path-state slots kept alive per GPU (about 0.8 KB each): the library default is a whole batch, <= 2^28
                        "paths_in_flight": args.paths_in_flight or "library default: min(batch, 2^28 paths) = 238 GB of path state at most, less when the device has less free",
                        "scene_commit_ms": b.info.get("build_ms")},
-            "roofline": roofline(b, acc, stc, args.steps),
+        }
+        if args.full:
+            out["roofline"] = roofline(b, acc, stc, args.steps)
+        out.update({
             "device_ms_per_step": acc["kernel_ms"] / args.steps,
             "gather_ms_per_step": gather_max / args.steps * 1e3 if world > 1 else 0.0,
             # what the collective layer actually saw (N > 1): backend as torch reports it ("nccl" = RCCL on ROCm) and the
@@ -545,13 +594,14 @@ def main():
             "mean_rays_per_path": rays_all / args.steps / (W * H * spp),
             # R1 extension incl. primary (integrator.rs:388), R2 shadow (:584), R3 MIS probe (:615), per step
             "rays": {"extension": rays3[0] / args.steps, "shadow": rays3[1] / args.steps, "probe": rays3[2] / args.steps},
-            "film_fnv1a": film_hash,
-            "film_matches_one_rank": film_ok,
-            "per_rank_device_ms": per_rank_ms,
-        }
+        })
+        if args.full:
+            out["film_fnv1a"] = film_hash
+            out["film_matches_one_rank"] = film_ok
+        out["per_rank_device_ms"] = per_rank_ms
         scene_for_cpu = b.scene
     b_main = b
-    if world == 1 and not args.no_extra and args.workload == "c4":
+    if args.full and world == 1 and not args.no_extra and args.workload == "c4":
         # the smaller single-GPU configs, same accounting (they are parity-test cases, not the headline)
         extra = []
         for name in ("c2", "c3"):
@@ -588,7 +638,7 @@ def main():
         f.close()
         out["extra"] = extra
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene_for_cpu, b_main.W, b_main.H)
         print(json.dumps(out), flush=True)
     b_main.close()

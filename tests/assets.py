@@ -4,7 +4,7 @@ tests/golden/assets/material/ holds data/material/models/Mesh000.obj and Mesh001
 (gzip-compressed OBJ text: data, not source) and data/material/textures/envmap.hdr (data/teapot/textures/envmap.hdr is
 the same file).  Mesh002.obj and the two teapot meshes are not in the checkout.  `material_dir(tmp)` unpacks them into the
 directory layout the presets read (models/*.obj, textures/envmap.hdr), so the GPU box -- which has no /root/reference --
-renders the real meshes too.
+renders the real meshes too.  SHA256SUMS there holds the digests of the reference checkout's three files.
 """
 import gzip
 import os

@@ -1,10 +1,11 @@
 #!/bin/bash
+T=$(mktemp -d); export T; trap 'rm -rf "$T"' EXIT   # scratch bench line (bench.py --full)
 run() {
   for wl in "$@"; do
-    timeout 900 python bench.py --workload $wl --no-cpu-baseline --no-extra --steps 3 --warmup 1 > gpurun_out/tmp.json 2>gpurun_out/tmp.err || { echo "FAILED"; tail -3 gpurun_out/tmp.err; continue; }
+    timeout 900 python bench.py --full --workload $wl --no-cpu-baseline --no-extra --steps 3 --warmup 1 > "$T"/bench.json 2>"$T"/bench.err || { echo "FAILED"; tail -3 "$T"/bench.err; continue; }
     python - $wl <<'PY'
-import json,sys
-d=json.load(open('gpurun_out/tmp.json'))
+import json,os,sys
+d=json.load(open(os.environ['T'] + '/bench.json'))
 r=d['roofline']; K=r['kernels']
 print('   %s Mrays/s %.0f ms %.2f trace %.2f classify %.2f shade %.2f'%(sys.argv[1],d['value'],d['ms_per_step'],K['k_trace']['ms_per_step'],K['k_classify']['ms_per_step'],K['k_shade']['ms_per_step']))
 PY

@@ -26,8 +26,8 @@ def stage(tag):
     rd_raw = t["FETCH_SIZE"] * 1024 / n
     wr = t["WRITE_SIZE"] * 1024 / n
     # every kernel of the profiled step: HBM bytes of the whole step (bench.py: roofline.hbm_frac_rocprof_step)
-    # The profiled command (tools/prof_pmc.sh: bench.py --steps 1 --warmup 0) renders the frame TWICE: the timed step and
-    # the instrumented counting pass bench.py always adds.  Kernels with a COUNT template flag exist once per pass
+    # The profiled command (tools/prof_pmc.sh: bench.py --full --steps 1 --warmup 0) renders the frame TWICE: the timed
+    # step and the instrumented counting pass that --full adds.  Kernels with a COUNT template flag exist once per pass
     # (k_trace<false, ..> / k_tail<.., false> = the timed step, <true, ..> / <.., true> = the counting pass, left out);
     # every other kernel ran in both passes under one name, so its sums are halved (the two passes do identical work).
     def passes(name):

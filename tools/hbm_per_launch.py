@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per launch: HBM-side traffic (rocprofv3 --pmc FETCH_SIZE x 2 on gfx950, WRITE_SIZE) over the launch's duration in the
-counter pass, for the first batch of the TIMED step of tools/prof_pmc.sh's command (bench.py --steps 1 --warmup 0).
+counter pass, for the first batch of the TIMED step of tools/prof_pmc.sh's command (bench.py --full --steps 1 --warmup 0).
 rocprofv3 serialises the dispatches while it counts, so every kernel is measured ALONE (in the product the class kernels
 run two at a time and the light kernel beside them and the next k_trace: DESIGN.md 12.8).
 

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/stats_$WL
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $REPO/bench.py --no-cpu-baseline --no-extra --workload $WL --steps 2 --warmup 1 "$@" > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $REPO/bench.py --full --no-cpu-baseline --no-extra --workload $WL --steps 2 --warmup 1 "$@" > $OUT/bench.json 2> $OUT/bench.err
 echo "rc=$?"
 python3 - $OUT <<'PY'
 import csv,glob,sys,re,os

@@ -10,7 +10,7 @@ rocprofv3 --list-avail 2>/dev/null | grep -o "\b\(TA\|TCP\|TD\)_[A-Z0-9_a-z]*" |
 BENCH_ARGS="$*"
 run_pass() {
   name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python3 $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra ${BENCH_ARGS} > $OUT/$name.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python3 $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra ${BENCH_ARGS} > $OUT/$name.log 2>&1
   echo "$name rc=$?"
 }
 run_pass ta1 TA_TA_BUSY_sum TA_BUSY_avr GRBM_GUI_ACTIVE

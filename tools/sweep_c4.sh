@@ -1,14 +1,15 @@
 #!/bin/bash
 # parameter sweeps on one workload (env knobs of abi.hip); one line per setting.  usage: tools/sweep_c4.sh [workload] [out tag]
+T=$(mktemp -d); export T; trap 'rm -rf "$T"' EXIT   # scratch bench line (bench.py --full)
 WL=${1:-c4}; TAG=${2:-r04}
 mkdir -p gpurun_out
 run() { # label, env...
   label=$1; shift
-  env "$@" timeout 600 python bench.py --workload $WL --no-cpu-baseline --no-extra --steps 2 --warmup 1 > gpurun_out/tmp.json 2>gpurun_out/tmp.err
+  env "$@" timeout 600 python bench.py --full --workload $WL --no-cpu-baseline --no-extra --steps 2 --warmup 1 > "$T"/bench.json 2>"$T"/bench.err
   python - "$label" <<'PY'
-import json,sys
+import json,os,sys
 try:
-    d=json.load(open('gpurun_out/tmp.json'))
+    d=json.load(open(os.environ['T'] + '/bench.json'))
     r=d['roofline']; K=r['kernels']
     print('%-34s Mrays/s %.0f ms %.1f trace %.1f classify %.1f shade %.1f launches %d'%(sys.argv[1],d['value'],d['ms_per_step'],K['k_trace']['ms_per_step'],K['k_classify']['ms_per_step'],K['k_shade']['ms_per_step'],r['k_trace_detail']['launches_per_step']))
 except Exception as e:
