@@ -399,6 +399,50 @@ int rt_render(rt_context* ctx, rt_scene* s, const rt_camera* cam, const rt_rende
 int rt_render_device(rt_context* ctx, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg,
                      double* d_rgb_sum, uint32_t* d_n, void* hip_stream, rt_stats* stats);
 
+/* ------------------------------------------------------- auxiliary films
+ * Optional per-pixel planes beside the radiance film (added without changing RT_ABI_VERSION: no existing
+ * struct or function changes).  Every pointer may be NULL = that plane is not produced.  Planes follow the
+ * film: zeroed whole-frame unless rt_render_cfg.flags has RT_RENDER_ACCUMULATE (then added to), and only the
+ * caller's pixels (window and rt_tile_owner tiles) are written.
+ *
+ * rgb_sq_sum is the per-sample second moment: sum over the same samples, in the same order, of L_c^2 (the
+ * staged binary64 radiance of whichever precision rendered), so that with rgb_sum and n a host has each
+ * pixel's variance: var = (sq - sum^2 / n) / (n - 1), standard error sqrt(var / n).
+ *
+ * The first-hit planes (guide buffers for a denoiser) are sums over the AOV samples of a pixel: the samples k
+ * of this call ([sample_first, sample_first + sample_count)) with k < aov_spp (0 = no limit), so progressive
+ * passes give the one-shot planes.  The first hit is the closest hit on [RT_SMALL, RT_INFINITY) of sample k's
+ * camera ray (the path's own).  Per AOV sample that hits a primitive:
+ *   albedo  Matte: k_d(u,v); Plastic: min(k_d + k_s, 1) per channel; Metal: FrConductor(1, eta, k);
+ *           Mirror: color; Glass, Light: (1,1,1)
+ *   normal  the shading normal of the hit record the path shades with (sh_n), unmodified
+ *   depth   t * |d|, d = the un-normalised camera direction (distance from the ray origin)
+ *   n_hit   1
+ * and 0 for a miss.  They are computed in binary64 without contraction whatever rt_render_cfg.precision is.
+ *
+ * Multi-device contexts (rt_context_create with n_devices > 1) return RT_ERR_UNSUPPORTED when any plane is
+ * requested.  Several processes with rt_render_cfg.tile_rank / tile_world need nothing special.          */
+typedef struct rt_aov_film {
+    double* rgb_sq_sum;  /* W*H*3: sum of L_c^2 over the samples of rgb_sum                              */
+    double* albedo_sum;  /* W*H*3: first-hit planes, sums over the AOV samples                           */
+    double* normal_sum;  /* W*H*3                                                                        */
+    double* depth_sum;   /* W*H                                                                          */
+    uint32_t* n_hit;     /* W*H: AOV samples whose camera ray hit a primitive                            */
+    uint32_t* n_aov;     /* W*H: AOV samples taken                                                       */
+    uint32_t aov_spp;    /* first-hit planes use samples k < aov_spp only; 0 = all                       */
+    uint32_t reserved;   /* 0                                                                            */
+    double aov_ms;       /* out: device time of the first-hit pass (HIP events; 0 when it did not run)   */
+} rt_aov_film;
+
+/* rt_render plus the planes of `aov` (host pointers, like the film; aov may be NULL).  With every plane
+ * NULL it is rt_render: the same film, n and counters.                                                   */
+int rt_render_aov(rt_context* ctx, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg, double* rgb_sum,
+                  uint32_t* n, rt_aov_film* aov, rt_stats* stats);
+/* rt_render_device plus the planes: `aov` is a HOST struct whose plane pointers are DEVICE buffers; all work
+ * on them is enqueued on hip_stream, like the film's.                                                    */
+int rt_render_aov_device(rt_context* ctx, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg,
+                         double* d_rgb_sum, uint32_t* d_n, rt_aov_film* aov, void* hip_stream, rt_stats* stats);
+
 /* Kernel-level parity entry: closest hit of BvhNode::intersects
  * (hittable.rs:591-634) for n host rays.                                      */
 int rt_intersect_batch(rt_context* ctx, rt_scene* s, const rt_ray* rays, uint64_t n, rt_hit* hits);

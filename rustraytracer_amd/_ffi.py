@@ -122,6 +122,15 @@ class rt_stats(C.Structure):
         return self.rays_extension + self.rays_shadow + self.rays_probe
 
 
+class rt_aov_film(C.Structure):
+    """Optional per-pixel planes of rt_render_aov / rt_render_aov_device (NULL pointer = plane not produced)."""
+    _fields_ = [
+        ("rgb_sq_sum", C.c_void_p), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p),
+        ("n_hit", C.c_void_p), ("n_aov", C.c_void_p), ("aov_spp", C.c_uint32), ("reserved", C.c_uint32),
+        ("aov_ms", C.c_double),
+    ]
+
+
 class rt_ray(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("dir", C.c_double * 3), ("tmin", C.c_double), ("tmax", C.c_double)]
 
@@ -144,7 +153,7 @@ ABI_SYMBOLS = [
     "rt_context_create", "rt_context_destroy", "rt_scene_create", "rt_scene_set_meshes",
     "rt_scene_set_primitives", "rt_scene_set_transforms", "rt_scene_set_materials", "rt_scene_set_textures",
     "rt_scene_set_lights", "rt_scene_commit", "rt_scene_commit_ex", "rt_scene_destroy", "rt_scene_get_info", "rt_render",
-    "rt_render_device", "rt_intersect_batch", "rt_intersect_batch_ex", "rt_resolve_rgb8", "rt_last_error", "rt_abi_version", "rt_tile_owner",
+    "rt_render_device", "rt_render_aov", "rt_render_aov_device", "rt_intersect_batch", "rt_intersect_batch_ex", "rt_resolve_rgb8", "rt_last_error", "rt_abi_version", "rt_tile_owner",
 ]
 HOST_SYMBOLS = [
     "rrh_scene_build", "rrh_scene_destroy", "rrh_scene_desc", "rrh_scene_camera", "rrh_scene_name",
@@ -211,6 +220,10 @@ def lib():
     L.rt_render.argtypes = [vp, vp, C.POINTER(rt_camera), C.POINTER(rt_render_cfg), vp, vp, C.POINTER(rt_stats)]
     L.rt_render_device.argtypes = [vp, vp, C.POINTER(rt_camera), C.POINTER(rt_render_cfg), vp, vp, vp,
                                    C.POINTER(rt_stats)]
+    L.rt_render_aov.argtypes = [vp, vp, C.POINTER(rt_camera), C.POINTER(rt_render_cfg), vp, vp, C.POINTER(rt_aov_film),
+                                C.POINTER(rt_stats)]
+    L.rt_render_aov_device.argtypes = [vp, vp, C.POINTER(rt_camera), C.POINTER(rt_render_cfg), vp, vp,
+                                       C.POINTER(rt_aov_film), vp, C.POINTER(rt_stats)]
     L.rt_intersect_batch.argtypes = [vp, vp, C.POINTER(rt_ray), C.c_uint64, C.POINTER(rt_hit)]
     L.rt_tile_owner.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.rt_tile_owner.restype = C.c_uint32

@@ -6,6 +6,7 @@ Mirrors the reference's call shape for the hot path:
                                         -> Context.render(scene, width, height, spp, max_depth)
 All compute goes through the HIP library; nothing here computes pixels on the CPU.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -62,6 +63,39 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+# rt_aov_film planes (include/rt_abi.h): name -> (struct field, channels, dtype)
+AOV_PLANES = {
+    "rgb_sq": ("rgb_sq_sum", 3, np.float64),  # sum of L_c^2 over the film's samples
+    "albedo": ("albedo_sum", 3, np.float64),  # first-hit planes: sums over the AOV samples
+    "normal": ("normal_sum", 3, np.float64),
+    "depth": ("depth_sum", 1, np.float64),
+    "n_hit": ("n_hit", 1, np.uint32),         # AOV samples whose camera ray hit a primitive
+    "n_aov": ("n_aov", 1, np.uint32),         # AOV samples taken
+}
+
+# Context.render_aov's result: the film, the planes (name -> array) and the first-hit pass's device time
+AovRender = collections.namedtuple("AovRender", "rgb_sum n planes stats aov_ms")
+
+
+def _plane_shape(name, height, width):
+    ch = AOV_PLANES[name][1]
+    return (height, width, ch) if ch > 1 else (height, width)
+
+
+def standard_error(rgb_sum, rgb_sq_sum, n):
+    """Per-pixel standard error of the mean radiance from (sum, sum of squares, n): sqrt(s^2 / n) with the unbiased sample
+    variance s^2 = (sq - sum^2 / n) / (n - 1), per channel.  NaN where n < 2 (no variance estimate)."""
+    rgb_sum = np.asarray(rgb_sum, dtype=np.float64)
+    rgb_sq_sum = np.asarray(rgb_sq_sum, dtype=np.float64)
+    nn = np.asarray(n, dtype=np.float64)
+    if rgb_sum.ndim == nn.ndim + 1:
+        nn = nn[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = (rgb_sq_sum - rgb_sum * rgb_sum / nn) / (nn - 1.0)
+        se = np.sqrt(np.maximum(var, 0.0) / nn)
+    return np.where(nn >= 2.0, se, np.nan)
 
 
 def make_cfg(width, height, spp, max_depth=MAX_DEPTH, seed=0, window=None, tile_rank=0, tile_world=1,
@@ -138,6 +172,65 @@ class Context:
         _check(F.lib().rt_render_device(self._h, gscene._h, camera, C.byref(cfg), C.c_void_p(d_rgb_ptr),
                                         C.c_void_p(d_n_ptr), C.c_void_p(stream or 0), C.byref(st)))
         return st
+
+    def render_aov(self, gscene, camera, cfg, planes=tuple(AOV_PLANES), aov_spp=0, film=None):
+        """rt_render_aov: the film plus the per-pixel planes named in `planes` (keys of AOV_PLANES).  Returns
+        AovRender(rgb_sum[H,W,3], n[H,W], {name: array}, rt_stats, aov_ms).  `film` = an earlier AovRender (or
+        (rgb_sum, n, planes)) when cfg carries RT_RENDER_ACCUMULATE: it is updated in place."""
+        planes = list(planes)
+        for name in planes:
+            if name not in AOV_PLANES:
+                raise ValueError(f"unknown plane {name!r} (one of {', '.join(AOV_PLANES)})")
+        if film is not None:
+            rgb, n, out = film[0], film[1], film[2]
+            assert rgb.dtype == np.float64 and n.dtype == np.uint32 and rgb.flags.c_contiguous and n.flags.c_contiguous
+            for name in planes:
+                a = out[name]
+                assert a.dtype == AOV_PLANES[name][2] and a.flags.c_contiguous and a.shape == _plane_shape(name, cfg.height, cfg.width)
+        else:
+            rgb = np.zeros((cfg.height, cfg.width, 3), dtype=np.float64)
+            n = np.zeros((cfg.height, cfg.width), dtype=np.uint32)
+            out = {name: np.zeros(_plane_shape(name, cfg.height, cfg.width), dtype=AOV_PLANES[name][2]) for name in planes}
+        aov = F.rt_aov_film()
+        aov.aov_spp = aov_spp
+        for name in planes:
+            setattr(aov, AOV_PLANES[name][0], out[name].ctypes.data)
+        st = F.rt_stats()
+        _check(F.lib().rt_render_aov(self._h, gscene._h, camera, C.byref(cfg), rgb.ctypes.data_as(C.c_void_p),
+                                     n.ctypes.data_as(C.c_void_p), C.byref(aov), C.byref(st)))
+        return AovRender(rgb, n, {name: out[name] for name in planes}, st, aov.aov_ms)
+
+    def render_aov_device(self, gscene, camera, cfg, d_rgb, d_n, planes, aov_spp=0, stream=None):
+        """rt_render_aov_device: film and planes in caller-owned device buffers -- torch tensors (checked for dtype, size
+        and contiguity) or raw device pointers.  planes: {name: tensor or pointer} (keys of AOV_PLANES).  Work is enqueued
+        on `stream` (a torch.cuda.Stream or a hipStream_t as int; None = the null stream).  Returns (rt_stats, aov_ms)."""
+        npix = cfg.width * cfg.height
+
+        def ptr(x, dtype, count):
+            if isinstance(x, int):
+                return x
+            import torch
+            want = {np.float64: torch.float64, np.uint32: torch.int32}[dtype]
+            ok_dtype = x.dtype == want or (dtype is np.uint32 and x.dtype == getattr(torch, "uint32", None))
+            if not (ok_dtype and x.is_contiguous() and x.numel() == count and x.is_cuda):
+                raise ValueError(f"device buffer: want a contiguous {want} tensor of {count} elements on the GPU")
+            return x.data_ptr()
+
+        aov = F.rt_aov_film()
+        aov.aov_spp = aov_spp
+        for name, buf in planes.items():
+            if name not in AOV_PLANES:
+                raise ValueError(f"unknown plane {name!r} (one of {', '.join(AOV_PLANES)})")
+            field, ch, dtype = AOV_PLANES[name]
+            setattr(aov, field, ptr(buf, dtype, npix * ch))
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        st = F.rt_stats()
+        _check(F.lib().rt_render_aov_device(self._h, gscene._h, camera, C.byref(cfg),
+                                            C.c_void_p(ptr(d_rgb, np.float64, npix * 3)),
+                                            C.c_void_p(ptr(d_n, np.uint32, npix)), C.byref(aov), C.c_void_p(stream or 0),
+                                            C.byref(st)))
+        return st, aov.aov_ms
 
     def intersect_batch(self, gscene, origins, dirs, tmin, tmax=F.RT_INFINITY, flags=0):
         """rt_intersect_batch_ex; flags: F.RT_INTERSECT_F32 | F.RT_INTERSECT_WAVEFRONT"""

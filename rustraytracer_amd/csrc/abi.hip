@@ -101,6 +101,8 @@ struct rt_context {
     size_t lf_capacity = 0;
     uint32_t* pix_list = nullptr;
     size_t pix_capacity = 0;
+    int32_t* aov_ovf = nullptr;  // k_aov: the traversal stacks' overflow entries, kOvfStack per thread of its grid
+    size_t aov_ovf_cap = 0;
     std::vector<hipEvent_t> events;
     TraceTune tune{24, 4, 0, 128};
     uint32_t tail_paths = 786432;  // switch to the fused tail kernel at or below this many live paths
@@ -352,6 +354,7 @@ int rt_context_destroy(rt_context* c) {
     if (c->batch) (void)hipFree(c->batch);
     if (c->lf) (void)hipFree(c->lf);
     if (c->pix_list) (void)hipFree(c->pix_list);
+    if (c->aov_ovf) (void)hipFree(c->aov_ovf);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return RT_OK;
@@ -1263,9 +1266,53 @@ static size_t batch_max() {  // camera samples per batch (film staging: 24 B eac
 }
 #define kBatchMax (batch_max())
 
+// The planes of an rt_aov_film on the device (rt_render_aov / rt_render_aov_device; one-device contexts only)
+struct AovReq {
+    double* sq = nullptr;  // rgb_sq_sum: k_resolve_sq instead of k_resolve
+    AovPlanes planes{};    // the first-hit planes: k_aov
+    uint32_t aov_spp = 0;
+    double aov_ms = 0.0;   // out
+    bool first_hit() const {
+        return planes.albedo || planes.normal || planes.depth || planes.n_hit || planes.n_aov;
+    }
+};
+
+// k_aov over the owned pixels for the AOV samples [a_first, a_end) of this pass, on `stream` after everything queued on it
+static int run_aov_pass(rt_context* c, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg, size_t NP, uint32_t a_first,
+                        uint32_t a_end, const AovPlanes& planes, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+    const rtk::AovKernel k = rtk::kernel_table().aov;
+    int occ = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, 256, 0));
+    // grid-stride: at most what is resident at once, so that the overflow stacks stay small (62 entries per thread)
+    const size_t blocks = std::max<size_t>(1, std::min<size_t>((NP + 255) / 256, (size_t)c->num_cus * std::max(1, occ)));
+    const size_t want = blocks * 256 * (size_t)kOvfStack;
+    if (c->aov_ovf_cap < want) {
+        if (c->aov_ovf) HIP_TRY(hipFree(c->aov_ovf));
+        c->aov_ovf = nullptr;
+        c->aov_ovf_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->aov_ovf, want * sizeof(int32_t)));
+        c->aov_ovf_cap = want;
+    }
+    ChunkDesc ck{};
+    ck.n_pixels = (uint32_t)NP;
+    ck.n_samples = a_end - a_first;
+    ck.pixel_base = 0;
+    ck.sample_base = a_first;
+    ck.width = cfg->width;
+    ck.height = cfg->height;
+    ck.seed = cfg->seed;
+    HIP_TRY(hipEventRecord(ev0, stream));
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, stream, s->dev, *cam, ck, c->pix_list, c->aov_ovf,
+                       planes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, stream));
+    return RT_OK;
+}
+
 // sub_rank / sub_world: device `sub_rank` of a several-device context takes every sub_world-th of the caller's tiles
 static int render_impl(rt_context* c, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg, double* d_rgb,
-                       uint32_t* d_n, hipStream_t stream, rt_stats* stats, uint32_t sub_rank = 0, uint32_t sub_world = 1) {
+                       uint32_t* d_n, hipStream_t stream, rt_stats* stats, uint32_t sub_rank = 0, uint32_t sub_world = 1,
+                       AovReq* aov = nullptr) {
     const uint32_t W = cfg->width, H = cfg->height;
     const uint32_t spp = next_pow2(cfg->spp);
     uint32_t x0 = cfg->x0, y0 = cfg->y0, x1 = cfg->x1, y1 = cfg->y1;
@@ -1295,6 +1342,15 @@ static int render_impl(rt_context* c, rt_scene* s, const rt_camera* cam, const r
     if (!(cfg->flags & RT_RENDER_ACCUMULATE)) {
         HIP_TRY(hipMemsetAsync(d_rgb, 0, sizeof(double) * 3 * (size_t)W * H, stream));
         HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * (size_t)W * H, stream));
+        if (aov) {  // the planes follow the film
+            const size_t npx = (size_t)W * H;
+            if (aov->sq) HIP_TRY(hipMemsetAsync(aov->sq, 0, sizeof(double) * 3 * npx, stream));
+            if (aov->planes.albedo) HIP_TRY(hipMemsetAsync(aov->planes.albedo, 0, sizeof(double) * 3 * npx, stream));
+            if (aov->planes.normal) HIP_TRY(hipMemsetAsync(aov->planes.normal, 0, sizeof(double) * 3 * npx, stream));
+            if (aov->planes.depth) HIP_TRY(hipMemsetAsync(aov->planes.depth, 0, sizeof(double) * npx, stream));
+            if (aov->planes.n_hit) HIP_TRY(hipMemsetAsync(aov->planes.n_hit, 0, sizeof(uint32_t) * npx, stream));
+            if (aov->planes.n_aov) HIP_TRY(hipMemsetAsync(aov->planes.n_aov, 0, sizeof(uint32_t) * npx, stream));
+        }
     }
     // progressive pass: samples [s_first, s_end) of every pixel
     const uint32_t s_first = std::min(cfg->sample_first, spp);
@@ -1317,6 +1373,25 @@ static int render_impl(rt_context* c, rt_scene* s, const rt_camera* cam, const r
     }
     double kernel_ms = 0.0, trace_ms = 0.0, shade_ms = 0.0, classify_ms = 0.0, light_ms = 0.0;
     uint64_t trace_launches = 0, shade_launches = 0;
+    // first-hit planes: the AOV samples of this pass are [s_first, a_end), before the path tracing, on the caller's stream
+    bool aov_ran = false;
+    hipEvent_t ev_aov0 = nullptr, ev_aov1 = nullptr;
+    if (aov) aov->aov_ms = 0.0;
+    if (aov && aov->first_hit() && NP > 0) {
+        const uint32_t a_end = aov->aov_spp ? std::min(s_end, aov->aov_spp) : s_end;
+        if (a_end > s_first) {
+            if (cfg->cancel && *cfg->cancel != 0) {
+                (void)hipStreamSynchronize(stream);
+                return fail(RT_ERR_CANCELLED, "rt_render: cancelled by the caller");
+            }
+            ev_aov0 = get_event(c->events, 3);
+            ev_aov1 = get_event(c->events, 4);
+            if (!ev_aov0 || !ev_aov1) return fail(RT_ERR_HIP, "hipEventCreate failed");
+            const int arc = run_aov_pass(c, s, cam, cfg, NP, s_first, a_end, aov->planes, stream, ev_aov0, ev_aov1);
+            if (arc != RT_OK) return arc;
+            aov_ran = true;
+        }
+    }
     if (NP > 0 && pass_spp > 0) {
         // batch shape: PB pixels x ns samples, at most kBatchMax camera samples (film staging size)
         uint32_t PB, ns;
@@ -1470,8 +1545,12 @@ static int render_impl(rt_context* c, rt_scene* s, const rt_camera* cam, const r
                     }
                 }
                 // every lane has drained (run_lane synchronises its stream): add the batch to the film
-                hipLaunchKernelGGL(rtk::kernel_table().resolve, dim3((npx + 255) / 256), dim3(256), 0, stream, c->lf,
-                                   ck, c->pix_list, d_rgb, d_n);
+                if (aov && aov->sq)
+                    hipLaunchKernelGGL(rtk::kernel_table().resolve_sq, dim3((npx + 255) / 256), dim3(256), 0, stream, c->lf,
+                                       ck, c->pix_list, d_rgb, d_n, aov->sq);
+                else
+                    hipLaunchKernelGGL(rtk::kernel_table().resolve, dim3((npx + 255) / 256), dim3(256), 0, stream, c->lf,
+                                       ck, c->pix_list, d_rgb, d_n);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -1503,6 +1582,11 @@ static int render_impl(rt_context* c, rt_scene* s, const rt_camera* cam, const r
         }
     } else {
         HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (aov_ran) {  // (the stream was synchronised above)
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev_aov0, ev_aov1));
+        aov->aov_ms = ms;
     }
     if (stats) {
         DevStats shards[kStatShards];
@@ -1776,6 +1860,97 @@ int rt_render(rt_context* c, rt_scene* s, const rt_camera* cam, const rt_render_
     }
     (void)hipFree(d_rgb);
     (void)hipFree(d_n);
+    return rc;
+}
+
+// ------------------------------------------------------------------ auxiliary films (rt_aov_film)
+static_assert(sizeof(rt_aov_film) == 64 && offsetof(rt_aov_film, aov_spp) == 48 && offsetof(rt_aov_film, aov_ms) == 56,
+              "rt_aov_film layout (rustraytracer_amd/_ffi.py)");
+static bool aov_any(const rt_aov_film* a) {
+    return a && (a->rgb_sq_sum || a->albedo_sum || a->normal_sum || a->depth_sum || a->n_hit || a->n_aov);
+}
+static AovReq aov_req(const rt_aov_film& a) {
+    AovReq r;
+    r.sq = a.rgb_sq_sum;
+    r.planes.albedo = a.albedo_sum;
+    r.planes.normal = a.normal_sum;
+    r.planes.depth = a.depth_sum;
+    r.planes.n_hit = a.n_hit;
+    r.planes.n_aov = a.n_aov;
+    r.aov_spp = a.aov_spp;
+    return r;
+}
+static int check_aov_args(rt_context* c, const rt_aov_film* aov) {
+    if (aov_any(aov) && !c->peers.empty())
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_aov: auxiliary planes are not produced by multi-device contexts");
+    return RT_OK;
+}
+
+int rt_render_aov_device(rt_context* c, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg, double* d_rgb_sum,
+                         uint32_t* d_n, rt_aov_film* aov, void* hip_stream, rt_stats* stats) {
+    int rc = check_render_args(c, s, cam, cfg);
+    if (rc != RT_OK) return rc;
+    if ((rc = check_aov_args(c, aov)) != RT_OK) return rc;
+    if (!d_rgb_sum || !d_n) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_device: null film pointer");
+    if (aov) aov->aov_ms = 0.0;
+    if (!aov_any(aov)) return render_any(c, s, cam, cfg, d_rgb_sum, d_n, (hipStream_t)hip_stream, stats);
+    AovReq req = aov_req(*aov);
+    rc = render_impl(c, s, cam, cfg, d_rgb_sum, d_n, (hipStream_t)hip_stream, stats, 0u, 1u, &req);
+    aov->aov_ms = req.aov_ms;
+    return rc;
+}
+
+int rt_render_aov(rt_context* c, rt_scene* s, const rt_camera* cam, const rt_render_cfg* cfg, double* rgb_sum, uint32_t* n,
+                  rt_aov_film* aov, rt_stats* stats) {
+    int rc = check_render_args(c, s, cam, cfg);
+    if (rc != RT_OK) return rc;
+    if ((rc = check_aov_args(c, aov)) != RT_OK) return rc;
+    if (aov) aov->aov_ms = 0.0;
+    if (!aov_any(aov)) return rt_render(c, s, cam, cfg, rgb_sum, n, stats);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)cfg->width * cfg->height;
+    const bool acc = (cfg->flags & RT_RENDER_ACCUMULATE) != 0;
+    if (acc && (!rgb_sum || !n)) return fail(RT_ERR_INVALID_ARG, "RT_RENDER_ACCUMULATE needs both film pointers");
+    // device copies of the film and of every requested plane: {host, device, bytes}
+    struct Buf {
+        void* host;
+        void* dev;
+        size_t bytes;
+    };
+    Buf bufs[8] = {{rgb_sum, nullptr, npix * 3 * sizeof(double)},      {n, nullptr, npix * sizeof(uint32_t)},
+                   {aov->rgb_sq_sum, nullptr, npix * 3 * sizeof(double)}, {aov->albedo_sum, nullptr, npix * 3 * sizeof(double)},
+                   {aov->normal_sum, nullptr, npix * 3 * sizeof(double)}, {aov->depth_sum, nullptr, npix * sizeof(double)},
+                   {aov->n_hit, nullptr, npix * sizeof(uint32_t)},       {aov->n_aov, nullptr, npix * sizeof(uint32_t)}};
+    auto release = [&] {
+        for (Buf& b : bufs)
+            if (b.dev) (void)hipFree(b.dev);
+    };
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 8 && e == hipSuccess; i++) {
+        if (i >= 2 && !bufs[i].host) continue;  // (the film is always rendered, like rt_render's)
+        e = hipMalloc(&bufs[i].dev, bufs[i].bytes);
+        if (e == hipSuccess && acc) e = hipMemcpy(bufs[i].dev, bufs[i].host, bufs[i].bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        release();
+        return fail(e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP, "rt_render_aov: device film: %s", hipGetErrorString(e));
+    }
+    AovReq req;
+    req.sq = (double*)bufs[2].dev;
+    req.planes.albedo = (double*)bufs[3].dev;
+    req.planes.normal = (double*)bufs[4].dev;
+    req.planes.depth = (double*)bufs[5].dev;
+    req.planes.n_hit = (uint32_t*)bufs[6].dev;
+    req.planes.n_aov = (uint32_t*)bufs[7].dev;
+    req.aov_spp = aov->aov_spp;
+    rc = render_impl(c, s, cam, cfg, (double*)bufs[0].dev, (uint32_t*)bufs[1].dev, c->stream, stats, 0u, 1u, &req);
+    aov->aov_ms = req.aov_ms;
+    for (int i = 0; i < 8 && rc == RT_OK; i++) {
+        if (!bufs[i].host) continue;
+        e = hipMemcpy(bufs[i].host, bufs[i].dev, bufs[i].bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, "rt_render_aov: film download failed: %s", hipGetErrorString(e));
+    }
+    release();
     return rc;
 }
 

@@ -32,6 +32,8 @@
 // Film: k_resolve sums each pixel's samples in sample order in f64 -- the order of
 // util::increment_color (util.rs:208-232) -- so images are bit-reproducible and
 // independent of how tiles are split over GPUs.
+// Auxiliary films (rt_aov_film): k_resolve_sq is k_resolve plus the per-sample second moment; k_aov, a pass of its own on
+// the caller's stream before the path tracing, re-traces the camera rays of the AOV samples for the first-hit planes.
 #include "shading.h"
 
 #ifndef RT_XCD_QUEUE
@@ -1456,6 +1458,106 @@ __global__ __launch_bounds__(256) void k_resolve(const double* __restrict__ lf, 
     rgb_sum[(size_t)pix * 3 + 1] = g;
     rgb_sum[(size_t)pix * 3 + 2] = b;
     n[pix] += ck.n_samples;
+}
+// k_resolve plus the per-sample second moment (rt_aov_film.rgb_sq_sum): the same film sums, and sq_sum += L_c^2 beside
+// them in the same order.  Launched instead of k_resolve only when the plane is requested.
+__global__ __launch_bounds__(256) void k_resolve_sq(const double* __restrict__ lf, ChunkDesc ck,
+                                                    const uint32_t* __restrict__ pix_list, double* rgb_sum, uint32_t* n,
+                                                    double* sq_sum) {
+    const uint32_t p_local = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p_local >= ck.n_pixels) return;
+    const uint32_t pix = pix_list[ck.pixel_base + p_local];
+    double r = rgb_sum[(size_t)pix * 3 + 0], g = rgb_sum[(size_t)pix * 3 + 1], b = rgb_sum[(size_t)pix * 3 + 2];
+    double r2 = sq_sum[(size_t)pix * 3 + 0], g2 = sq_sum[(size_t)pix * 3 + 1], b2 = sq_sum[(size_t)pix * 3 + 2];
+    for (uint32_t s = 0; s < ck.n_samples; s++) {
+        const double* q = lf + (size_t)(s * ck.n_pixels + p_local) * 3;  // kernels.hip: film_put
+        const double q0 = q[0], q1 = q[1], q2 = q[2];
+        r += q0;
+        g += q1;
+        b += q2;
+        r2 += q0 * q0;
+        g2 += q1 * q1;
+        b2 += q2 * q2;
+    }
+    rgb_sum[(size_t)pix * 3 + 0] = r;
+    rgb_sum[(size_t)pix * 3 + 1] = g;
+    rgb_sum[(size_t)pix * 3 + 2] = b;
+    sq_sum[(size_t)pix * 3 + 0] = r2;
+    sq_sum[(size_t)pix * 3 + 1] = g2;
+    sq_sum[(size_t)pix * 3 + 2] = b2;
+    n[pix] += ck.n_samples;
+}
+
+// ------------------------------------------------------------------- first-hit planes (rt_aov_film)
+// One thread per pixel (grid-stride: the grid is what is resident at once), looping over the pass's AOV samples
+// [ck.sample_base, ck.sample_base + ck.n_samples) in sample order with the sums in registers, so that the planes do
+// not depend on how the pixels are split.  The camera ray is k_generate's (camera_sample, same RNG key), its closest hit
+// the run-to-completion traversal of k_intersect_batch on [SMALL, inf), its record the one the shading kernels build.
+// Binary64 whatever the render's precision: compiled once, in the f64 namespace.
+// The traversal stack's overflow part lives in `ovf` (kOvfStack entries per thread of the grid) instead of a private
+// array: no scratch.
+__global__ __launch_bounds__(256) void k_aov(DevScene sc, rt_camera cam, ChunkDesc ck, const uint32_t* __restrict__ pix_list,
+                                             int32_t* __restrict__ ovf, AovPlanes out) {
+    __shared__ int2 lds_stack[kLdsStack * 256];
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    TravStack ts;
+    ts.lds = &lds_stack[threadIdx.x];
+    ts.ovf = ovf + (size_t)tid * kOvfStack;
+    // texture k of a material, as mat_tex (shading.h) looks it up, without the call
+    auto tex = [&](const DevMat& dm, int k, double u, double v) -> D3 {
+        if (dm.solid_mask & (1u << k)) return d3(dm.col[k][0], dm.col[k][1], dm.col[k][2]);
+        return texture_value_inl(sc, dm.tex[k], u, v);
+    };
+    ChunkDesc one = ck;  // camera_sample's view of sample k of pixel p_local: a batch of one sample
+    one.n_samples = 1;
+    for (uint32_t p_local = tid; p_local < ck.n_pixels; p_local += gridDim.x * blockDim.x) {
+        const size_t pix = pix_list[ck.pixel_base + p_local];
+        D3 alb = d3(0.0, 0.0, 0.0), nrm = d3(0.0, 0.0, 0.0);
+        double dep = 0.0;
+        if (out.albedo) alb = d3(out.albedo[pix * 3 + 0], out.albedo[pix * 3 + 1], out.albedo[pix * 3 + 2]);
+        if (out.normal) nrm = d3(out.normal[pix * 3 + 0], out.normal[pix * 3 + 1], out.normal[pix * 3 + 2]);
+        if (out.depth) dep = out.depth[pix];
+        uint32_t hits = 0;
+        for (uint32_t s = 0; s < ck.n_samples; s++) {
+            one.sample_base = ck.sample_base + s;
+            D3 o, d;
+            uint64_t rng;
+            camera_sample(cam, one, pix_list, p_local, o, d, rng);
+            double t;
+            const int32_t prim = closest_hit<false>(sc, o, d, kSmall, kInf, t, ts, nullptr);
+            HitRec h;
+            if (prim < 0 || !prim_intersects(sc, prim, o, d, kSmall, kInf, h)) continue;  // miss: adds 0 everywhere
+            hits++;
+            if (out.albedo) {
+                const DevMat& dm = sc.mats[h.mat];
+                D3 a = d3(1.0, 1.0, 1.0);  // glass, light
+                if (dm.m.kind == RT_MAT_MATTE || dm.m.kind == RT_MAT_MIRROR) {
+                    a = tex(dm, 0, h.u, h.v);
+                } else if (dm.m.kind == RT_MAT_PLASTIC) {
+                    const D3 s2 = tex(dm, 0, h.u, h.v) + tex(dm, 1, h.u, h.v);
+                    a = d3(s2.x < 1.0 ? s2.x : 1.0, s2.y < 1.0 ? s2.y : 1.0, s2.z < 1.0 ? s2.z : 1.0);
+                } else if (dm.m.kind == RT_MAT_METAL) {
+                    a = fr_conductor(1.0, tex(dm, 0, h.u, h.v), tex(dm, 1, h.u, h.v));
+                }
+                alb = alb + a;
+            }
+            nrm = nrm + h.sh_n;
+            dep += h.t * dm_sqrt(d.x * d.x + d.y * d.y + d.z * d.z);
+        }
+        if (out.albedo) {
+            out.albedo[pix * 3 + 0] = alb.x;
+            out.albedo[pix * 3 + 1] = alb.y;
+            out.albedo[pix * 3 + 2] = alb.z;
+        }
+        if (out.normal) {
+            out.normal[pix * 3 + 0] = nrm.x;
+            out.normal[pix * 3 + 1] = nrm.y;
+            out.normal[pix * 3 + 2] = nrm.z;
+        }
+        if (out.depth) out.depth[pix] = dep;
+        if (out.n_hit) out.n_hit[pix] += hits;
+        if (out.n_aov) out.n_aov[pix] += ck.n_samples;
+    }
 }
 
 // util.rs:400-408, 441-471: film -> ACES approx -> gamma 2.2 -> 8 bit (next-row f1)

@@ -235,6 +235,15 @@ struct ChunkDesc {
     uint64_t seed;
 };
 
+// The first-hit planes of rt_aov_film (include/rt_abi.h) that k_aov writes; a null pointer = plane not produced.
+struct AovPlanes {
+    double* albedo;   // W*H*3
+    double* normal;   // W*H*3
+    double* depth;    // W*H
+    uint32_t* n_hit;  // W*H
+    uint32_t* n_aov;  // W*H
+};
+
 struct TraceTune {
     int refill_lanes;  // refill when at least this many lanes are idle (<= 64)
     int node_bias;     // a node step runs when lanes_at_nodes * node_bias >= lanes_at_leaves * 4 (4 = plain majority)

@@ -73,7 +73,8 @@ RTD D3 hdr_value(const rt_texture& t, double u, double v) {
     return d3(((double)(q & 0xffu) + 0.5) * sc / 256.0, ((double)((q >> 8) & 0xffu) + 0.5) * sc / 256.0,
               ((double)((q >> 16) & 0xffu) + 0.5) * sc / 256.0);
 }
-RTDN D3 texture_value(const DevScene& sc, uint32_t index, double u, double v) {
+// (texture_value_inl: the same lookup inlined into its caller -- k_aov, which must make no calls: a call frame is scratch)
+RTD D3 texture_value_inl(const DevScene& sc, uint32_t index, double u, double v) {
 #pragma unroll 1
     for (int depth = 0; depth < 8; depth++) {
         const rt_texture& t = sc.texs[index];
@@ -85,6 +86,7 @@ RTDN D3 texture_value(const DevScene& sc, uint32_t index, double u, double v) {
     if (t.kind == RT_TEX_HDR) return hdr_value(t, u, v);
     return d3(t.color[0], t.color[1], t.color[2]);
 }
+RTDN D3 texture_value(const DevScene& sc, uint32_t index, double u, double v) { return texture_value_inl(sc, index, u, v); }
 
 // bxdf.rs:113-136
 RTD double fr_dielectric(double cos_theta_i, double eta_i, double eta_t) {

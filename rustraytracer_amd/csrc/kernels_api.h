@@ -26,6 +26,8 @@ typedef void (*GenKernel)(PathState, rt_camera, ChunkDesc, const uint32_t*, uint
 typedef void (*PlanKernel)(Ctl*, BatchCtl*, uint32_t, uint32_t, unsigned long long, DevStats*);
 typedef void (*IntersectKernel)(DevScene, const rt_ray*, uint64_t, rt_hit*);
 typedef void (*ResolveKernel)(const double*, ChunkDesc, const uint32_t*, double*, uint32_t*);
+typedef void (*ResolveSqKernel)(const double*, ChunkDesc, const uint32_t*, double*, uint32_t*, double*);
+typedef void (*AovKernel)(DevScene, rt_camera, ChunkDesc, const uint32_t*, int32_t*, AovPlanes);
 typedef void (*TonemapKernel)(const double*, const uint32_t*, uint64_t, uint8_t*);
 
 struct KernelTable {
@@ -42,6 +44,8 @@ struct KernelTable {
     ClassifyScanKernel classify_scan;
     ClassifyScatterKernel classify_scatter;
     ResolveKernel resolve;
+    ResolveSqKernel resolve_sq;  // k_resolve + the second moment (rt_aov_film.rgb_sq_sum)
+    AovKernel aov;               // the first-hit planes of rt_aov_film (binary64 in both precisions)
     TonemapKernel tonemap;
 };
 KernelTable& kernel_table();  // abi.hip (filled by the static initialisers of tu/*.hip)

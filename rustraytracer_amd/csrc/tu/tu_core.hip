@@ -28,6 +28,8 @@ struct Reg {
 #if !RT_TU_F32
         t.plan = K::k_plan;
         t.resolve = K::k_resolve;
+        t.resolve_sq = K::k_resolve_sq;
+        t.aov = K::k_aov;
         t.tonemap = K::k_tonemap;
 #endif
     }

@@ -127,3 +127,31 @@ class FilmGather:
                 flat_rgb[self.all_idx[r]] = bufs[r][:kr, :3]
                 flat_n[self.all_idx[r]] = bufs[r][:kr, 3].to(flat_n.dtype)
         return rgb_sum, n
+
+    def gather_planes(self, *planes, dst=0):
+        """Auxiliary planes of this rank (rt_aov_film: [H,W] or [H,W,C] tensors of any dtype whose values f64 holds exactly,
+        e.g. f64 sums and i32 counts) gathered like `gather`: each rank sends its own pixels, packed, in one payload; on
+        `dst` the planes become the full planes.  Returns the planes."""
+        if self.world == 1:
+            return planes
+        assert dst == 0
+        flats = [p.view(self.height * self.width, -1) for p in planes]
+        chans = [f.shape[1] for f in flats]
+        pay = torch.zeros((self.max_count, sum(chans)), dtype=torch.float64, device=self.device)
+        k = self.count[self.rank]
+        col = 0
+        for f, ch in zip(flats, chans):
+            pay[:k, col:col + ch] = f[self.own].to(torch.float64)
+            col += ch
+        bufs = [torch.empty_like(pay) for _ in range(self.world)] if self.rank == dst else None
+        dist.gather(pay, bufs, dst=dst)
+        if self.rank == dst:
+            for r in range(self.world):
+                if r == dst:
+                    continue
+                kr = self.count[r]
+                col = 0
+                for f, ch in zip(flats, chans):
+                    f[self.all_idx[r]] = bufs[r][:kr, col:col + ch].to(f.dtype)
+                    col += ch
+        return planes
